@@ -15,7 +15,10 @@ messages to P0/P1 and the finalize. `value` = secret-shared 64-bit mults
 job; the metric is quoted "per party" because every party takes part in
 every multiplication.
 
-The JSON line also carries:
+A plain run sets up, warms up, times --steps steps, writes the last step's
+product if --dump-outputs is given, and prints the JSON line. Every other
+leg runs only with --full: the plaintext check of the product, and the legs
+behind these further entries of the JSON line:
   roofline      -- the share-GEMM kernel: int8 MFMA ops per launch
                    (144*M*N*K) / its average launch time,
                    measured with HIP events on the party streams, vs the
@@ -44,6 +47,12 @@ PEAK_HBM_GBS = 8000.0  # MI355X HBM3E spec
 # timed LR iterations (host-API bound, so a longer sample for a stable figure)
 LR_ITERS = 300
 
+# --dump-outputs writes at most this much
+DUMP_LIMIT_BYTES = 64 << 20
+# and tops the pre-warm's step count up to a multiple of this (0.3 s of C2
+# steps is about 1200 steps, so runs on slower and faster builds land on 4096)
+DUMP_STEP_QUANTUM = 4096
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -53,6 +62,19 @@ def parse():
     ap.add_argument("--k", type=int, default=1024)
     ap.add_argument("--n", type=int, default=1024)
     ap.add_argument("--decimal", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the plaintext check of the product, the "
+                         "share-GEMM roofline pass and kernel breakdown, the binary (C3) leg, the C1/C4/C5 and "
+                         "conversion extras, the party-process layouts and the CPU baselines (minutes, not "
+                         "seconds). Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed to DIR/product.npy: the "
+                         "product the three parties' result shares reveal, as float64 (fixed point / 2^decimal), "
+                         f"row-major; above {DUMP_LIMIT_BYTES >> 20} MB a fixed seeded sample of its entries. The "
+                         "operands are the same in every run. The truncation's last bit depends on how many steps "
+                         f"ran before, so the pre-warm is topped up to a multiple of {DUMP_STEP_QUANTUM} steps: runs "
+                         "with the same arguments then write the same array (were the counts to differ, entries "
+                         "would differ by at most 4 * 2^-decimal)")
     ap.add_argument("--binary-rows", type=int, default=1 << 20)
     ap.add_argument("--binary-steps", type=int, default=30)
     ap.add_argument("--binary-cpu-rows", type=int, default=1 << 18, help="rows of the CPU baseline sample (C3)")
@@ -211,6 +233,28 @@ def timed(sess, steps, pg, secs=0.0, warmup=0):
     t1 = time.perf_counter()
     barrier(pg)
     return allmax(pg, t1 - t0)
+
+
+def dump_outputs(sess, path, rows, cols, decimal):
+    """What the last step of `sess` (a C2 session) computed, as a caller of
+    asyncMul receives it and reveals it: the three parties' first result
+    shares summed modulo 2^64, the fixed-point product, written as float64
+    (exact: the product of operands in [-8, 8) has far fewer than 53 bits)
+    to path/product.npy. Above DUMP_LIMIT_BYTES a sample of the entries at
+    fixed seeded positions, in row-major order."""
+    import numpy as np
+
+    total = np.zeros(rows * cols, dtype=np.uint64)
+    for party in range(3):
+        total += sess.result(party)[0].view(np.uint64)
+    prod = total.view(np.int64).astype(np.float64) / float(1 << decimal)
+    limit = DUMP_LIMIT_BYTES // 8
+    if prod.size > limit:
+        prod = prod[np.sort(np.random.default_rng(0).choice(prod.size, limit, replace=False))]
+    else:
+        prod = prod.reshape(rows, cols)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "product.npy"), prod)
 
 
 def cpu_mul_procs_s(mode, reps):
@@ -635,6 +679,8 @@ def main():
     world, rank, local, pg = dist_setup()
     from aby3_amd import native as nt
 
+    if args.dump_outputs and args.deployment != "replicas":
+        raise SystemExit("bench: --dump-outputs writes the replicas deployment's product only")
     if args.deployment == "parties":
         return main_parties(args, world, rank, local, pg, nt)
     if args.deployment == "rowsplit":
@@ -649,19 +695,33 @@ def main():
     if args.gemm_turns:
         nt.lib().mfma_turn(1)
     # only the share-GEMM launches carry timing events (the roofline kernel);
-    # digit and epilogue times come from a second, separately probed pass
+    # digit and epilogue times come from a second, separately probed pass.
+    # A plain run keeps those events although only --full reports them: the
+    # timed steps are the same steps with and without --full
     progress("C2 asyncMul + truncation session")
     sess = nt.Session(nt.JOB_MUL_TRUNC, [M, K, N, D, 1], devices=(dev, dev, dev), probe=1 << nt.PROBE_GEMM)
-    # correctness first, then the warmup steps right before the timed region
-    # (a host-side reveal between warmup and timing lets the clocks drop)
+    # correctness first (--full), then the warmup steps right before the timed
+    # region (a host-side reveal between warmup and timing lets the clocks drop)
     sess.run(2)
-    if not sess.check():
+    if args.full and not sess.check():
         raise SystemExit("bench: revealed product does not match the plaintext")
     # time-based pre-warm, then the W warmup steps right before the timed region
     # (after the host-side reveal the clocks have dropped; ~50 ms of steps
     # bring them back: scripts/steady_state.py)
     t_pw = time.perf_counter()
     prewarm_steps = prewarm(sess, args.prewarm_s)
+    if args.dump_outputs and prewarm_steps:
+        # every step advances the parties' randomness, which decides the
+        # last bit of the truncation: top the time-based count up to a fixed
+        # one, so that the last step's product is the same from run to run
+        # (a smaller quantum where the steps are long: at most 4 s of them)
+        quantum, step_s = DUMP_STEP_QUANTUM, (time.perf_counter() - t_pw) / prewarm_steps
+        while quantum > 1 and quantum * step_s > 4.0:
+            quantum //= 4
+        pad = -prewarm_steps % quantum
+        if pad:
+            sess.run(pad)
+        prewarm_steps += pad
     prewarm_s = time.perf_counter() - t_pw
     sess.run(args.warmup)
     sess.probe_reset()
@@ -673,34 +733,12 @@ def main():
     dt = allmax(pg, t1 - t0)
     info = sess.info()
     ovl_ms, ovl_n = sess.probe(nt.PROBE_GEMM)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sess, args.dump_outputs, M, N, D)
     sess.close()
-    # Roofline pass: in the timed region the three co-located parties' GEMMs
-    # overlap on the one GPU (faster together), so a launch's span there also
-    # covers the CUs spent on the other two; here they take turns and each
-    # launch's HIP-event span is the kernel's own duration.
-    progress("C2 roofline pass (GEMMs take turns)")
-    nt.lib().mfma_turn(1)
-    with nt.Session(nt.JOB_MUL_TRUNC, [M, K, N, D, 1], devices=(dev, dev, dev), probe=1 << nt.PROBE_GEMM) as rp:
-        rp.run(5)
-        prewarm(rp, 0.2)
-        rp.probe_reset()
-        rp.run(30)
-        gemm_ms, gemm_n = rp.probe(nt.PROBE_GEMM)
-    nt.lib().mfma_turn(1 if args.gemm_turns else 0)
-    # kernel-time breakdown and the device-side local-compute fraction from a
-    # separate pass with every family probed (event pairs around every launch
-    # perturb the timing, so not the timed run)
-    c2_local = compute_fraction(nt, nt.JOB_MUL_TRUNC, [M, K, N, D, 1], dev, 10)
-    breakdown = {name: c2_local["family_ms_per_step"][fam] for name, fam in
-                 (("share_gemm", nt.PROBE_GEMM), ("digit_planes", nt.PROBE_DIGITS),
-                  ("trunc_epilogue", nt.PROBE_EPILOGUE))}
 
     mults = info["mults_per_step"]
     value = world * args.steps * mults / dt
-    gemm_avg_s = gemm_ms / max(gemm_n, 1) / 1e3
-    achieved_tops = info["gemm_int8_ops"] / gemm_avg_s / 1e12 if gemm_avg_s > 0 else 0.0
-    cfg = {"m": M, "k": K, "n": N}
-    traffic = load_pmc("share_gemm", cfg)
     out = {
         "metric": "secret-shared 64-bit mults/sec (matmul + binary-AND) per party, 3 parties on 3 MI355X",
         "value": value,
@@ -723,6 +761,40 @@ def main():
             "global_batch": world,
             "parallelism": f"replicas{world}",
         },
+        "host_recv_wait_us_per_step": info["host_recv_wait_us"],
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if pg is not None:
+            pg.destroy_process_group()
+        return
+
+    # Roofline pass: in the timed region the three co-located parties' GEMMs
+    # overlap on the one GPU (faster together), so a launch's span there also
+    # covers the CUs spent on the other two; here they take turns and each
+    # launch's HIP-event span is the kernel's own duration.
+    progress("C2 roofline pass (GEMMs take turns)")
+    nt.lib().mfma_turn(1)
+    with nt.Session(nt.JOB_MUL_TRUNC, [M, K, N, D, 1], devices=(dev, dev, dev), probe=1 << nt.PROBE_GEMM) as rp:
+        rp.run(5)
+        prewarm(rp, 0.2)
+        rp.probe_reset()
+        rp.run(30)
+        gemm_ms, gemm_n = rp.probe(nt.PROBE_GEMM)
+    nt.lib().mfma_turn(1 if args.gemm_turns else 0)
+    # kernel-time breakdown and the device-side local-compute fraction from a
+    # separate pass with every family probed (event pairs around every launch
+    # perturb the timing, so not the timed run)
+    c2_local = compute_fraction(nt, nt.JOB_MUL_TRUNC, [M, K, N, D, 1], dev, 10)
+    breakdown = {name: c2_local["family_ms_per_step"][fam] for name, fam in
+                 (("share_gemm", nt.PROBE_GEMM), ("digit_planes", nt.PROBE_DIGITS),
+                  ("trunc_epilogue", nt.PROBE_EPILOGUE))}
+    gemm_avg_s = gemm_ms / max(gemm_n, 1) / 1e3
+    achieved_tops = info["gemm_int8_ops"] / gemm_avg_s / 1e12 if gemm_avg_s > 0 else 0.0
+    cfg = {"m": M, "k": K, "n": N}
+    traffic = load_pmc("share_gemm", cfg)
+    out.update({
         "roofline": {
             "bound": "mfma",
             "kernel": "k_share_gemm16s (int8 MFMA 16x16x64, 36 digit pairs as 20 two-pair MFMAs per block and stage)",
@@ -757,8 +829,7 @@ def main():
         # kernels, minus their in-kernel waits for peers), from a probed pass
         "local_compute_fraction": c2_local["local_compute_fraction"],
         "local_compute": c2_local,
-        "host_recv_wait_us_per_step": info["host_recv_wait_us"],
-    }
+    })
 
     if not args.no_binary:
         progress("C3 binary session")

@@ -3,12 +3,12 @@
 # bench, then separate FETCH_SIZE / WRITE_SIZE passes of the two jobs.
 R=$GRAFT_REPO_ROOT
 TAG=${1:-r01}
-O=$R/gpurun_out/$TAG
+O=${EVIDENCE_OUT:-$R/evidence}/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # GEMMs take turns in this run, so every launch span is the kernel's own (bench.py roofline pass)
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o run -- \
-    python3 $R/bench.py --steps 30 --warmup 10 --no-extras --no-cpu-baseline --gemm-turns > $O/trace.log 2>&1 || exit $?
+    python3 $R/bench.py --full --steps 30 --warmup 10 --no-extras --no-cpu-baseline --gemm-turns > $O/trace.log 2>&1 || exit $?
 for job in mul msb; do
   for c in FETCH_SIZE WRITE_SIZE; do
     # counter passes serialise kernels: the channels see ROCPROF_COUNTER_COLLECTION and use events

@@ -6,6 +6,7 @@
 // Three forked processes on the null device (gen_nulldev.py), built with
 // -fsanitize=address by tests/test_host_asan.py.
 #include "Channel.h"
+#include "Link.h"
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -46,6 +47,20 @@ static int party_main(int p, const std::string& tag) {
         std::printf("FAIL party %d: small messages %llu %llu\n", p, (unsigned long long)x, (unsigned long long)y);
         return 1;
     }
+    // leave together (Session.cpp leaveTogether): a party that is done must
+    // not exit while a slower peer still waits on its other link -- that
+    // peer's watchdog takes a process gone without closing for a failure
+    const u64 token = 0xC105Eull;
+    u64 s = 0, t = 0;
+    c.mNext.asyncSendCopy(token);
+    c.mPrev.asyncSendCopy(token);
+    c.mNext.recv(s);
+    c.mPrev.recv(t);
+    if (s != token || t != token) {
+        std::printf("FAIL party %d: closing tokens %llx %llx\n", p, (unsigned long long)s, (unsigned long long)t);
+        return 1;
+    }
+    LinkEnd::closeAll();
     return 0;
 }
 

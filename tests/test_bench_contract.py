@@ -1,6 +1,6 @@
 """The bench line's contract, checked on CPU against the committed round
-evidence (profiles/r*_bench.json, written by `python bench.py` on the GPU
-box): the keys the driver reads, the roofline and cpu_baseline objects, and
+evidence (profiles/r*_bench.json, written by `python bench.py --full` on an
+MI355X): the keys the driver reads, the roofline and cpu_baseline objects, and
 the arithmetic between them (value = mults per step / time; frac =
 achieved / peak; the rocprofv3 kernel stats of the same tree agree with the
 in-bench launch time)."""
