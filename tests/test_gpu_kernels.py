@@ -156,9 +156,13 @@ def test_mul_local(gpu, mode, M, K, N, with_zs):
 
 
 def test_gemm_digit_extremes(gpu):
-    """Operands at the digit-carry corners: all-ones, 2^63, 0x7f/0x80 bytes."""
+    """k_small_gemm (the VALU kernel: 64^3 = 2^18 terms is below the 2^23
+    threshold, so no digits and no MFMA) on operands at the carry corners:
+    all-ones, 2^63, 0x7f/0x80 bytes. The digit path sees these values in
+    test_gpu_gemm_edges.py."""
     M = K = N = 64
-    vals = np.array([-1, -(2**63), 2**63 - 1, 0x7F7F7F7F7F7F7F7F, -0x7F7F7F7F7F7F7F80, 0x8080808080808080 - 2**64,
+    assert gpu.dll.aby3g_mul_prefers_fused(nt.MUL_GEMM, M, K, N) == 1
+    vals = np.array([-1, -(2**63), 2**63 - 1, 0x7F7F7F7F7F7F7F7F, -0x7F7F7F7F7F7F7F80, 0x7F7F7F7F7F7F7F80,
                      1, 0], dtype=np.int64)
     rng = np.random.default_rng(9)
     A = vals[rng.integers(0, len(vals), 2 * M * K)]
