@@ -530,7 +530,10 @@ int aby3g_lin_copy_out(const aby3g_wire_src* srcs, uint32_t nsrc, uint64_t rows,
  * batches read the input wires [in_lo, in_hi) (at most
  * ABY3G_LEVEL_IN_MAX_WIRES) from LDS and every other wire from mem. The
  * input wires reach mem only when write_inputs != 0 (a later level reads
- * them). Sources' wire_rows name their wires in mem as for
+ * them); otherwise mem keeps what it held there. A wire of [in_lo, in_hi)
+ * that no source with terms covers reads as zero, and with write_inputs it
+ * is written as zero too: every wire of the range, in both shares, is
+ * stored. Sources' wire_rows name their wires in mem as for
  * aby3g_bits_to_wires_lin; a source without terms is all zero and must have
  * constant 0 (rejected otherwise). post: the level's AND shares handed over
  * in-kernel (aby3g_handoff), or NULL. */

@@ -218,18 +218,41 @@ def test_mul_trunc_local(gpu, mode, M, K, N):
     assert np.array_equal(c[:n], e0) and np.array_equal(c[n:], e1)
 
 
-@pytest.mark.parametrize("party", [0, 1, 2])
-def test_trunc_finalize(gpu, party):
-    n, d = 999, 13
-    za, zb, zo, C = rnd(1, n), rnd(2, n), rnd(3, n), rnd(4, 2 * n)
+def _trunc_finalize_case(gpu, party, n, za_word_offset=0):
+    """C[party] += (z_a + z_b + z_own) >> d against numpy; party 2 leaves the
+    garbage in C alone. z_a is handed over za_word_offset words into its buffer."""
+    d = 13
+    za, zb, zo, C = rnd(1, n), rnd(2, n), rnd(3, n), rnd(4, 2 * n + 1)
     Cd = dev(C)
-    gpu.trunc_finalize(party, P(dev(za)), P(dev(zb)), P(dev(zo)), d, P(Cd), n, None)
+    zad = dev(np.concatenate([np.zeros(za_word_offset, dtype=np.int64), za]))
+    assert zad.data_ptr() % 16 == 0
+    gpu.trunc_finalize(party, ctypes.c_void_p(zad.data_ptr() + 8 * za_word_offset), P(dev(zb)), P(dev(zo)), d, P(Cd),
+                       n, None)
     s = (za.view(np.uint64) + zb.view(np.uint64) + zo.view(np.uint64)).view(np.int64) >> d
     exp = C.copy()
     if party < 2:
         exp[party * n:(party + 1) * n] = (exp[party * n:(party + 1) * n].view(np.uint64) + s.view(np.uint64)).view(
             np.int64)
     assert np.array_equal(host(Cd), exp)
+
+
+@pytest.mark.parametrize("party", [0, 1, 2])
+def test_trunc_finalize(gpu, party):
+    _trunc_finalize_case(gpu, party, 999)  # odd n: the one-word kernel
+
+
+# k_trunc_finalize2 takes two elements a thread on a grid capped at 8192 x 256
+# threads (ew.hip: ew_grid): from n / 2 > 8192 * 256 on its grid-stride loop wraps
+TRUNC_WRAP_N = 2 * 8192 * 256 + 1554
+
+
+@pytest.mark.parametrize("n,za_word_offset", [(1000, 0), (1000, 1), (TRUNC_WRAP_N, 0)],
+                         ids=["vector", "even_n_unaligned_za", "grid_stride_wraps"])
+@pytest.mark.parametrize("party", [0, 1, 2])
+def test_trunc_finalize_paths(gpu, party, n, za_word_offset):
+    """Even n with every pointer 16-byte aligned runs k_trunc_finalize2 for
+    parties 0 and 1; z_a one word off falls back to the one-word kernel."""
+    _trunc_finalize_case(gpu, party, n, za_word_offset)
 
 
 def _bits_ref(x, nbits, words):
@@ -655,3 +678,82 @@ def test_lincomb_bitops(gpu):
     exp = np.zeros(n, dtype=np.int64)
     exp[idx] = a
     assert np.array_equal(host(o), exp)
+
+
+@pytest.mark.parametrize("cols", [1, 37, 128])
+def test_gather_rows(gpu, cols):
+    """dst[s][i][:] = src[s][idx[i]][:] for both shares: repeated indices and the last row."""
+    import torch
+
+    rows, n = 53, 41
+    src = rnd(cols, 2 * rows * cols).reshape(2, rows, cols)
+    idx = np.random.default_rng(cols).integers(0, rows, size=n).astype(np.int32)
+    idx[:4] = [rows - 1, 7, 7, 0]
+    g = rnd(5, 2 * n * cols + 1)
+    dst = dev(g)
+    idxd = torch.from_numpy(idx).to("cuda")  # a local: alive until the kernel has run
+    gpu.i64_gather_rows(P(dev(src)), rows, cols, P(idxd), n, P(dst), None)
+    got = host(dst)
+    assert np.array_equal(got[:-1].reshape(2, n, cols), src[:, idx, :])
+    assert got[-1] == g[-1], "wrote past the end of dst"
+
+
+@pytest.mark.parametrize("absent", ["none", "a", "b", "c", "mask"])
+@pytest.mark.parametrize("with_idx", [False, True])
+@pytest.mark.parametrize("unit", [1, 3])
+def test_xor_gather_units(gpu, unit, with_idx, absent):
+    """out[i] = a[g] ^ b[g] ^ c[g] ^ mask over units of `unit` words, g = idx[i]
+    or i, each operand left out in turn."""
+    import torch
+
+    units = 1237
+    ops = {k: rnd(10 + j, units * unit).view(np.uint64) for j, k in enumerate("abc")}
+    mask = rnd(13, unit).view(np.uint64)
+    idx = np.random.default_rng(14).permutation(units).astype(np.int32)
+    g = rnd(15, units * unit + 1)
+    out = dev(g)
+    ptr = {k: (None if k == absent else P(dev(v))) for k, v in ops.items()}
+    idxd = torch.from_numpy(idx).to("cuda")  # a local: alive until the kernel has run
+    gpu.u64_xor_gather_units(units, unit, P(idxd) if with_idx else None, ptr["a"], ptr["b"], ptr["c"],
+                             None if absent == "mask" else P(dev(mask)), P(out), None)
+    exp = np.zeros((units, unit), dtype=np.uint64)
+    for k, v in ops.items():
+        if k != absent:
+            v = v.reshape(units, unit)
+            exp ^= v[idx] if with_idx else v
+    if absent != "mask":
+        exp ^= mask
+    got = host(out)
+    assert np.array_equal(got[:-1].view(np.uint64).reshape(units, unit), exp)
+    assert got[-1] == g[-1], "wrote past the end of out"
+
+
+def test_xor_gather_units_rejects_in_place_gather(gpu):
+    import torch
+
+    a = dev(rnd(1, 30))
+    idx = torch.arange(10, dtype=torch.int32, device="cuda")
+    for k in range(3):
+        ops = [P(a) if j == k else None for j in range(3)]
+        with pytest.raises(nt.NativeError, match="in place"):
+            gpu.u64_xor_gather_units(10, 3, P(idx), *ops, None, P(a), None)
+    gpu.u64_xor_gather_units(10, 3, None, P(a), None, None, None, P(a), None)  # without idx it may
+    assert np.array_equal(host(a), rnd(1, 30))
+
+
+@pytest.mark.parametrize("rows,cols", [(1, 1), (64, 64), (65, 63), (256, 128), (100, 37)])
+def test_transpose(gpu, rows, cols):
+    """dst[s] = src[s]^T for both shares, through 64 x 64 tiles."""
+    src = rnd(rows + cols, 2 * rows * cols).reshape(2, rows, cols)
+    g = rnd(6, 2 * rows * cols + 1)
+    dst = dev(g)
+    gpu.i64_transpose(P(dev(src)), rows, cols, P(dst), None)
+    got = host(dst)
+    assert np.array_equal(got[:-1].reshape(2, cols, rows), src.transpose(0, 2, 1))
+    assert got[-1] == g[-1], "wrote past the end of dst"
+
+
+def test_transpose_rejects_in_place(gpu):
+    a = dev(rnd(1, 2 * 8 * 8))
+    with pytest.raises(nt.NativeError, match="in-place"):
+        gpu.i64_transpose(P(a), 8, 8, P(a), None)
