@@ -23,6 +23,7 @@
 #include <map>
 #include <mutex>
 #include "epilogue.h"
+#include "skinny.h"
 
 #ifndef ABY3G_TILE_GROUP
 #define ABY3G_TILE_GROUP 4  // row panels per tile group (tile_of)
@@ -47,6 +48,8 @@ inline u64 roundup(u64 x, u64 m) { return (x + m - 1) / m * m; }
 
 // GEMMs up to this many product terms run on the VALU (k_small_gemm), with
 // no digit split and no MFMA; the epilogue then works in place on the product.
+// (Products of at most kSkinnyMaxN columns may take the streaming skinny route
+// of skinny.hip ahead of both; plan_skinny decides.)
 constexpr u64 kSmallGemmTerms = 1ull << 23;
 inline bool small_gemm(u64 M, u64 K, u64 N) { return M * N * K <= kSmallGemmTerms; }
 
@@ -580,6 +583,22 @@ void check_ws(const GemmPlan& p, void* ws, size_t bytes) {
     ABY3G_REQUIRE(ws != nullptr && bytes >= p.total, "workspace too small (see aby3g_mul_workspace_bytes)");
 }
 
+// The streaming skinny route (skinny.hip) of a GEMM-mode product, if it takes one.
+inline SkinnyPlan skinny_route(u64 M, u64 K, u64 N) { return plan_skinny(M, K, N, small_gemm(M, K, N)); }
+
+// Runs the skinny product. Tall: into `direct`, returned as one slab; long:
+// split-K slabs in the workspace, for the caller's epilogue to sum.
+SrcSlabs run_skinny_route(const SkinnyPlan& sp, const i64* A, const i64* B, u64 M, u64 K, u64 N, i64* direct,
+                          void* ws, size_t bytes, hipStream_t s) {
+    if (sp.form == SKINNY_TALL) {
+        run_skinny(sp, A, B, M, K, N, direct, s);
+        return SrcSlabs{direct, 1, M * N};
+    }
+    ABY3G_REQUIRE(ws != nullptr && bytes >= sp.bytes, "workspace too small (see aby3g_mul_workspace_bytes)");
+    run_skinny(sp, A, B, M, K, N, (i64*)ws, s);
+    return SrcSlabs{(const i64*)ws, sp.splits, M * N};
+}
+
 }  // namespace
 
 }  // namespace aby3g
@@ -600,11 +619,14 @@ int aby3g_mfma_turn(int on) {
 }
 
 int aby3g_mul_prefers_fused(int mode, uint64_t M, uint64_t K, uint64_t N) {
-    return mode != ABY3G_MUL_GEMM || small_gemm(M, K, N);
+    return mode != ABY3G_MUL_GEMM || small_gemm(M, K, N) || skinny_route(M, K, N).form != SKINNY_NONE;
 }
 
 size_t aby3g_mul_workspace_bytes(int mode, uint64_t M, uint64_t K, uint64_t N) {
-    if (mode != ABY3G_MUL_GEMM || small_gemm(M, K, N)) return 0;
+    if (mode != ABY3G_MUL_GEMM) return 0;
+    const SkinnyPlan sp = skinny_route(M, K, N);
+    if (sp.form != SKINNY_NONE) return sp.bytes;
+    if (small_gemm(M, K, N)) return 0;
     return plan_gemm(M, K, N).total;
 }
 
@@ -619,6 +641,14 @@ int aby3g_mul_local(int mode, const int64_t* A, const int64_t* B, int64_t* C0, u
             if (zs)
                 launch_finish_zero_share(src, n, *zs, C0, S(stream));
             else
+                launch_finish_plain(src, n, C0, S(stream));
+            return;
+        }
+        if (const SkinnyPlan sp = skinny_route(M, K, N); sp.form != SKINNY_NONE) {
+            const SrcSlabs src = run_skinny_route(sp, A, B, M, K, N, C0, workspace, workspace_bytes, S(stream));
+            if (zs)
+                launch_finish_zero_share(src, n, *zs, C0, S(stream));
+            else if (src.nsplit > 1 || src.P != C0)
                 launch_finish_plain(src, n, C0, S(stream));
             return;
         }
@@ -658,6 +688,11 @@ int aby3g_mul_trunc_local(int mode, const int64_t* A, const int64_t* B, uint64_t
             launch_finish_trunc(src, *ts, n, d, nullptr, C, C + n, z, S(stream));
             return;
         }
+        if (const SkinnyPlan sp = skinny_route(M, K, N); sp.form != SKINNY_NONE) {
+            const SrcSlabs src = run_skinny_route(sp, A, B, M, K, N, z, workspace, workspace_bytes, S(stream));
+            launch_finish_trunc(src, *ts, n, d, nullptr, C, C + n, z, S(stream));
+            return;
+        }
         if (small_gemm(M, K, N)) {
             run_small_gemm(A, B, M, K, N, z, S(stream));  // product into z, then z -= r in place
             launch_finish_trunc(SrcSlabs{z, 1, n}, *ts, n, d, nullptr, C, C + n, z, S(stream));
@@ -688,6 +723,12 @@ int aby3g_mul_sub_local(int mode, const int64_t* A, const int64_t* B, const int6
         if (mode == ABY3G_MUL_HADAMARD) {
             if (sub_ready) ABY3G_CHECK_HIP(hipStreamWaitEvent(S(stream), (hipEvent_t)sub_ready, 0));
             launch_finish_plain(SrcHadamardMinus{A, A + n, B, B + n, sub}, n, out, S(stream));
+            return;
+        }
+        if (const SkinnyPlan sp = skinny_route(M, K, N); sp.form != SKINNY_NONE) {
+            const SrcSlabs src = run_skinny_route(sp, A, B, M, K, N, out, workspace, workspace_bytes, S(stream));
+            if (sub_ready) ABY3G_CHECK_HIP(hipStreamWaitEvent(S(stream), (hipEvent_t)sub_ready, 0));
+            launch_finish_plain(SrcSlabsMinus{src.P, src.nsplit, n, sub}, n, out, S(stream));
             return;
         }
         if (small_gemm(M, K, N)) {

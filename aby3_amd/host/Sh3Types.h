@@ -56,6 +56,10 @@ public:
     void shareFromHost(int s, const i64* src);
     void setZero();
     void copyFrom(const SharedMat& o);  // deep copy on this party's stream
+    // This matrix becomes `o`'s memory seen as rows x cols (rows * cols ==
+    // o.size()): no copy, nothing owned -- `o` must outlive it and keep its
+    // size. A column's transpose is such a view.
+    void viewOf(const SharedMat& o, u64 rows, u64 cols);
 
 protected:
     DeviceBuffer mBuf;

@@ -404,6 +404,84 @@ int aby3h_lr_dataset(uint64_t n, uint64_t dim, uint64_t D, int64_t* X, int64_t* 
     });
 }
 
+int aby3h_sim_linear(int device, uint64_t n, uint64_t d, uint64_t B, uint64_t D, uint64_t aB, uint64_t iters,
+                     const int64_t* X, const int64_t* Y, const uint64_t* batches, int64_t* out_w_shares,
+                     int64_t* out_w_plain) {
+    return guarded([&] {
+        if (!n || !d || !B) throw std::runtime_error("empty regression shapes");
+        i64Matrix xm = hostMat(X, n, d), ym = hostMat(Y, n, 1), w0(d, 1);
+        std::vector<u32> idx(iters * B);
+        for (u64 i = 0; i < idx.size(); ++i) {
+            if (batches[i] >= n) throw std::runtime_error("batch index out of range");
+            idx[i] = (u32)batches[i];
+        }
+        run3(
+            device,
+            [&](SimParty& p) {
+                si64Matrix sX(n, d), sY(n, 1), sW(d, 1);
+                shareIn(p, xm, sX);
+                shareIn(p, ym, sY);
+                shareIn(p, w0, sW);
+                aby3ML ml(p.rt, p.enc, p.eval, D);
+                SgdState st;
+                for (u64 t = 0; t < iters; ++t)
+                    sgdLinearStep(ml, sX, sY, sW, std::vector<u32>(idx.begin() + t * B, idx.begin() + (t + 1) * B), aB,
+                                  st);
+                putShares(p.idx, sW, out_w_shares);
+                i64Matrix r;
+                p.enc.revealAll(p.rt, sW, r).get();
+                if (p.idx == 0 && out_w_plain) std::memcpy(out_w_plain, r.mData.data(), 8 * d);
+            },
+            true);
+    });
+}
+
+int aby3h_sim_model_score(int device, int kind, uint64_t n, uint64_t d, uint64_t D, const int64_t* X,
+                          const int64_t* Y, const int64_t* w, int64_t* out_pred_shares, int64_t* out_pred_plain,
+                          int64_t* out_l2_shares, double* out_score) {
+    return guarded([&] {
+        if (!n || !d) throw std::runtime_error("empty model shapes");
+        if (kind != 0 && kind != 1) throw std::runtime_error("unknown model kind");
+        i64Matrix xm = hostMat(X, n, d), ym = hostMat(Y, n, 1), wm = hostMat(w, d, 1);
+        run3(
+            device,
+            [&](SimParty& p) {
+                si64Matrix sX(n, d), sY(n, 1), sW(d, 1), pred, l2;
+                shareIn(p, xm, sX);
+                shareIn(p, ym, sY);
+                shareIn(p, wm, sW);
+                aby3ML ml(p.rt, p.enc, p.eval, D);
+                double score[2] = {0, 0};
+                if (kind == 0) {
+                    score[0] = test_linearModel(ml, sW, sX, sY, &pred, &l2);
+                } else {
+                    const auto s = test_logisticModel(ml, sW, sX, sY, &pred, &l2);
+                    score[0] = s[0];
+                    score[1] = s[1];
+                }
+                putShares(p.idx, pred, out_pred_shares);
+                putShares(p.idx, l2, out_l2_shares);
+                i64Matrix r;
+                p.enc.revealAll(p.rt, pred, r).get();
+                if (p.idx == 0 && out_pred_plain) std::memcpy(out_pred_plain, r.mData.data(), 8 * n);
+                if (p.idx == 0 && out_score) std::memcpy(out_score, score, sizeof score);
+            },
+            true);
+    });
+}
+
+int aby3h_linear_dataset(uint64_t n, uint64_t dim, uint64_t D, int64_t* X, int64_t* Y, double* model) {
+    return guarded([&] {
+        auto m = logisticModel(dim);
+        if (model) std::memcpy(model, m.data(), 8 * dim);
+        if (!X && !Y) return;
+        i64Matrix x, y;
+        linearModelGen(m, n, D, x, y);
+        if (X) std::memcpy(X, x.data(), 8 * x.size());
+        if (Y) std::memcpy(Y, y.data(), 8 * n);
+    });
+}
+
 int aby3h_lr_batches(uint64_t n, uint64_t B, uint64_t iters, uint64_t* out) {
     return guarded([&] {
         BatchSampler s(n);

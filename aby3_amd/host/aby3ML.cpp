@@ -621,6 +621,119 @@ void SGD_Logistic(RegressionParam& params, aby3ML& engine, const si64Matrix& X, 
         sgdLogisticStep(engine, X, Y, w, sampler.next(), B, aB, st);
 }
 
+void sgdLinearStep(aby3ML& ml, const si64Matrix& X, const si64Matrix& Y, si64Matrix& w, const u32* batchIdx, u64 B,
+                   u64 aB, SgdState& st) {
+    Gpu& g = ml.mRt.gpu();
+    const u64 d = X.cols();
+    // extractBatch (Regression.h:42-58)
+    st.XX.resize(B, d);
+    st.YY.resize(B, 1);
+    GPU_CALL(aby3g_i64_gather_rows(X.data(), X.rows(), d, batchIdx, B, st.XX.data(), g.stream()));
+    GPU_CALL(aby3g_i64_gather_rows(Y.data(), Y.rows(), 1, batchIdx, B, st.YY.data(), g.stream()));
+    ml.mul(st.XX, w, st.xw);  // error = XX * w - YY
+    st.err.resize(B, 1);
+    GPU_CALL(aby3g_i64_lincomb(2 * B, 1, st.xw.data(), -1, st.YY.data(), 0, st.err.data(), g.stream()));
+    st.XXt.resize(d, B);  // XX^T
+    GPU_CALL(aby3g_i64_transpose(st.XX.data(), B, d, st.XXt.data(), g.stream()));
+    ml.mulTruncate(st.XXt, st.err, st.update, aB);  // update = XX^T error / 2^(D + aB)
+    GPU_CALL(aby3g_i64_lincomb(2 * d, 1, w.data(), -1, st.update.data(), 0, w.data(), g.stream()));
+}
+
+void sgdLinearStep(aby3ML& ml, const si64Matrix& X, const si64Matrix& Y, si64Matrix& w,
+                   const std::vector<u32>& batchIdx, u64 aB, SgdState& st) {
+    Gpu& g = ml.mRt.gpu();
+    const u64 B = batchIdx.size();
+    if (st.idx.bytes() < B * 4) st.idx.reset(g, B * 4);
+    toDevice(st.idx.data(), batchIdx.data(), B * 4, g);
+    sgdLinearStep(ml, X, Y, w, st.idx.as<u32>(), B, aB, st);
+}
+
+void predLinear(aby3ML& ml, const si64Matrix& X, const si64Matrix& w, si64Matrix& out) { ml.mul(X, w, out); }
+
+void predLogistic(aby3ML& ml, const si64Matrix& X, const si64Matrix& w, si64Matrix& out) {
+    si64Matrix xw;
+    ml.mul(X, w, xw);
+    ml.logisticFunc(xw, out);
+}
+
+namespace {
+
+// l2 = mul(error^T, error) of error = pred - y, revealed as fixed point D over the rows
+double l2Score(aby3ML& e, const si64Matrix& pred, const si64Matrix& y, si64Matrix& l2) {
+    if (pred.rows() != y.rows() || y.cols() != 1 || pred.cols() != 1) throw std::runtime_error(LOCATION);
+    Gpu& g = e.mRt.gpu();
+    const u64 n = y.rows();
+    si64Matrix err(n, 1), errT;
+    GPU_CALL(aby3g_i64_lincomb(2 * n, 1, pred.data(), -1, y.data(), 0, err.data(), g.stream()));
+    errT.viewOf(err, 1, n);  // a column's transpose: the same memory
+    e.mul(errT, err, l2);
+    i64Matrix r;
+    e.mEnc.revealAll(e.mRt.noDependencies(), l2, r).get();
+    return (double)r(0) / (double)(1ull << e.mD) / (double)n;
+}
+
+}  // namespace
+
+double test_linearModel(aby3ML& engine, const si64Matrix& W, const si64Matrix& x, const si64Matrix& y,
+                        si64Matrix* pred, si64Matrix* l2) {
+    si64Matrix xw, l2s;
+    si64Matrix& p = pred ? *pred : xw;
+    predLinear(engine, x, W, p);
+    return l2Score(engine, p, y, l2 ? *l2 : l2s);
+}
+
+std::array<double, 2> test_logisticModel(aby3ML& engine, const si64Matrix& W, const si64Matrix& x,
+                                         const si64Matrix& y, si64Matrix* pred, si64Matrix* l2) {
+    si64Matrix fxw, l2s;
+    si64Matrix& p = pred ? *pred : fxw;
+    predLogistic(engine, x, W, p);
+    const double score = l2Score(engine, p, y, l2 ? *l2 : l2s);
+    i64Matrix pp, yy;
+    engine.mEnc.revealAll(engine.mRt.noDependencies(), p, pp).get();
+    engine.mEnc.revealAll(engine.mRt.noDependencies(), y, yy).get();
+    // the reference compares the revealed fixed-point values, as doubles, with 0.5
+    const double scale = (double)(1ull << engine.mD);
+    u64 count = 0;
+    for (u64 i = 0; i < pp.size(); ++i) count += ((double)pp(i) / scale > 0.5) == ((double)yy(i) / scale > 0.5);
+    return {score, (double)count / (double)y.rows()};
+}
+
+void SGD_Linear(RegressionParam& params, aby3ML& engine, const si64Matrix& X, const si64Matrix& Y, si64Matrix& w,
+                const si64Matrix* X_test, const si64Matrix* Y_test, std::vector<double>* scores) {
+    if (X.rows() != Y.rows() || Y.cols() != 1) throw std::runtime_error(LOCATION);
+    const u64 B = params.mBatchSize;
+    // the learning rate in log2 form: truncate this many bits (Regression.h:139)
+    const u64 aB = (u64)std::log2(1 / (params.mLearningRate / (double)B));
+    DeviceBatchSampler sampler(engine.mRt.gpu(), X.rows(), B);
+    SgdState st;
+    for (u64 i = 0; i < params.mIterations; ++i) {
+        sgdLinearStep(engine, X, Y, w, sampler.next(), B, aB, st);
+        if (X_test && Y_test && i % 1000 == 0) {
+            const double score = test_linearModel(engine, w, *X_test, *Y_test);
+            if (scores) scores->push_back(score);
+        }
+    }
+}
+
+void linearModelGen(const std::vector<double>& model, u64 n, u64 D, i64Matrix& X, i64Matrix& Y) {
+    const u64 dim = model.size();
+    std::default_random_engine generator;
+    std::normal_distribution<double> distribution(1.0, 1.0);
+    X.resize(n, dim);
+    Y.resize(n, 1);
+    const double scale = (double)(1ull << D);
+    std::vector<double> row(dim);
+    for (u64 i = 0; i < n; ++i) {
+        for (u64 j = 0; j < dim; ++j) row[j] = distribution(generator);
+        const double noise = distribution(generator);
+        double y = 0;
+        for (u64 j = 0; j < dim; ++j) y += row[j] * model[j];
+        y += noise;
+        for (u64 j = 0; j < dim; ++j) X(i, j) = (i64)(row[j] * scale);
+        Y(i, 0) = (i64)(y * scale);
+    }
+}
+
 MlSeeds mlSeeds(int pIdx) {
     block enc[3], ev[3];
     for (u64 i = 0; i < 3; ++i) {

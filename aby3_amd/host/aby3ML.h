@@ -5,6 +5,7 @@
 #include "Sh3Evaluator.h"
 #include "Sh3Piecewise.h"
 #include <algorithm>
+#include <array>
 #include <vector>
 
 namespace aby3 {
@@ -149,6 +150,56 @@ struct RegressionParam {
     double mLearningRate = 0;
 };
 void SGD_Logistic(RegressionParam& params, aby3ML& engine, const si64Matrix& X, const si64Matrix& Y, si64Matrix& w);
+
+// ---- linear regression, model scoring and prediction ----------------------
+
+// One SGD_Linear iteration (Regression.h:145-168) on the batch of B row
+// indices at device pointer `batchIdx`, op by op on the gather, transpose and
+// mul primitives:
+//   XX, YY = extractBatch; err = mul(XX, w) - YY;
+//   update = mulTruncate(XX^T, err, aB); w = w - update
+void sgdLinearStep(aby3ML& ml, const si64Matrix& X, const si64Matrix& Y, si64Matrix& w, const u32* batchIdx, u64 B,
+                   u64 aB, SgdState& st);
+// Host-index convenience form: uploads the indices (and waits for the upload).
+void sgdLinearStep(aby3ML& ml, const si64Matrix& X, const si64Matrix& Y, si64Matrix& w,
+                   const std::vector<u32>& batchIdx, u64 aB, SgdState& st);
+
+// test_linearModel (Regression.h:94-107): err = mul(x, W) - y, l2 = mul(err^T,
+// err), returns reveal(l2(0)) / rows as fixed point D. mul is the engine's
+// product with shift D; err^T is err's own memory (a column's transpose).
+// Every party calls it (the reveals are revealAll). pred / l2: optional, the
+// shares of x W and of l2.
+double test_linearModel(aby3ML& engine, const si64Matrix& W, const si64Matrix& x, const si64Matrix& y,
+                        si64Matrix* pred = nullptr, si64Matrix* l2 = nullptr);
+// test_logisticModel (Regression.h:188-214): the same on fxw =
+// logisticFunc(mul(x, W)); returns {reveal(l2(0)) / rows, the share of rows
+// where reveal(fxw) > 0.5 agrees with reveal(y) > 0.5}. pred: fxw.
+std::array<double, 2> test_logisticModel(aby3ML& engine, const si64Matrix& W, const si64Matrix& x,
+                                         const si64Matrix& y, si64Matrix* pred = nullptr, si64Matrix* l2 = nullptr);
+
+// pred_linear / pred_logistic (main-pred.cpp:350-359). Their bodies are not
+// in the reference (they live in its absent Lynx engine); these are the
+// computations test_linearModel / test_logisticModel and main-linear.cpp:122
+// perform: out = mul(X, w), and out = logisticFunc(mul(X, w)).
+void predLinear(aby3ML& ml, const si64Matrix& X, const si64Matrix& w, si64Matrix& out);
+void predLogistic(aby3ML& ml, const si64Matrix& X, const si64Matrix& w, si64Matrix& out);
+
+// SGD_Linear (Regression.h:111-185): the training loop on device shares, a
+// DeviceBatchSampler batch and one sgdLinearStep per iteration, aB = log2(B /
+// rate). With test data, test_linearModel's value is appended to *scores at
+// i % 1000 == 0, where the reference prints it.
+void SGD_Linear(RegressionParam& params, aby3ML& engine, const si64Matrix& X, const si64Matrix& Y, si64Matrix& w,
+                const si64Matrix* X_test = nullptr, const si64Matrix* Y_test = nullptr,
+                std::vector<double>* scores = nullptr);
+
+// LinearModelGen::sample (LinearModelGen.cpp:17-40) with setModel's defaults
+// noise = sd = 1: a default-seeded libstdc++ default_random_engine and
+// normal_distribution(1, 1), per row its features then its noise,
+// Y = X model + noise, stored as fixed point D (i64(v * 2^D)). The model is
+// logisticModel(dim), the same draw as main-linear.cpp:37-45. The reference
+// forms X model with Eigen, whose summation order can move Y's last
+// fixed-point bit; the reference does not pin that bit.
+void linearModelGen(const std::vector<double>& model, u64 n, u64 D, i64Matrix& X, i64Matrix& Y);
 // aby3ML::init (aby3ML.cpp:4-17): party i's seed toBlock(i); PRNG(seed)'s
 // first block is its Sh3Encryptor seed, the second its Sh3Evaluator seed,
 // each exchanged with the neighbours (Sh3ShareGen.h:25-31): returns the

@@ -132,6 +132,7 @@ _SIGS = {
     "aby3g_trunc_tuple": (c_int, [POINTER(TruncStreams), c_uint64, ctypes.c_uint, c_void_p, c_void_p, c_void_p]),
     "aby3g_mul_prefers_fused": (c_int, [c_int, c_uint64, c_uint64, c_uint64]),
     "aby3g_mfma_turn": (c_int, [c_int]),
+    "aby3g_skinny_route": (c_int, [c_int]),
     "aby3g_mul_sub_local": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64,
                                     c_uint64, c_void_p, c_size_t, c_void_p]),
     "aby3g_mul_trunc_local": (c_int, [c_int, c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, ctypes.c_uint,
@@ -268,6 +269,11 @@ _HOST_SIGS = {
                              c_void_p, c_void_p, c_void_p]),
     "aby3h_lr_dataset": (c_int, [c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "aby3h_lr_batches": (c_int, [c_uint64, c_uint64, c_uint64, c_void_p]),
+    "aby3h_sim_linear": (c_int, [c_int, c_uint64, c_uint64, c_uint64, c_uint64, c_uint64, c_uint64, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "aby3h_sim_model_score": (c_int, [c_int, c_int, c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "aby3h_linear_dataset": (c_int, [c_uint64, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "aby3h_sim_shuffle": (c_int, [c_int, c_int, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
     "aby3h_sim_merge": (c_int, [c_int, c_int, c_void_p, c_uint64, c_uint64, c_void_p, c_void_p, c_void_p]),
 }
@@ -528,6 +534,41 @@ class sim:
         return sh.reshape(3, 2, d), w
 
     @classmethod
+    def linear(cls, X, Y, batches, D=16, aB=16, device=0):
+        """SGD_Linear iterations on (X [n][d], Y [n]) fixed point, one per row
+        of batches [iters][B]; returns (w shares [3][2][d], revealed w)."""
+        np = cls._np()
+        X = np.ascontiguousarray(X, np.int64)
+        Y = np.ascontiguousarray(Y, np.int64).reshape(-1)
+        batches = np.ascontiguousarray(batches, np.uint64)
+        n, d = X.shape
+        iters, B = batches.shape
+        sh = np.zeros(6 * d, np.int64)
+        w = np.zeros(d, np.int64)
+        cls._call("aby3h_sim_linear", device, n, d, B, D, aB, iters, cls._p(X), cls._p(Y), cls._p(batches),
+                  cls._p(sh), cls._p(w))
+        return sh.reshape(3, 2, d), w
+
+    @classmethod
+    def model_score(cls, kind, X, Y, w, D=16, device=0):
+        """test_linearModel (kind 0) / test_logisticModel (kind 1) of the model
+        w [d] on (X [n][d], Y [n]), fixed point D. Returns a dict: pred_shares
+        [3][2][n], pred [n] (revealed), l2_shares [3][2][1], score (the
+        function's return values: l2 / n, and for kind 1 the accuracy)."""
+        np = cls._np()
+        X = np.ascontiguousarray(X, np.int64)
+        Y = np.ascontiguousarray(Y, np.int64).reshape(-1)
+        w = np.ascontiguousarray(w, np.int64).reshape(-1)
+        n, d = X.shape
+        if Y.size != n or w.size != d:
+            raise ValueError("sim.model_score: Y and w do not match X")
+        ps, pp = np.zeros(6 * n, np.int64), np.zeros(n, np.int64)
+        ls, sc = np.zeros(6, np.int64), np.zeros(2, np.float64)
+        cls._call("aby3h_sim_model_score", device, kind, n, d, D, cls._p(X), cls._p(Y), cls._p(w), cls._p(ps),
+                  cls._p(pp), cls._p(ls), cls._p(sc))
+        return dict(pred_shares=ps.reshape(3, 2, n), pred=pp, l2_shares=ls.reshape(3, 2, 1), score=sc)
+
+    @classmethod
     def merge(cls, lists, mode=0, dim=0, shares=False, device=0):
         """The merge network (aby3h_sim_merge): mode 0 odd_even_multi_merge of
         separately shared lists, 1 the flat form (singletons: the sort),
@@ -557,6 +598,20 @@ def lr_dataset(n: int, dim: int = 128, D: int = 16):
     m = np.zeros(dim, np.float64)
     if host().aby3h_lr_dataset(n, dim, D, X.ctypes.data_as(c_void_p), Y.ctypes.data_as(c_void_p),
                                m.ctypes.data_as(c_void_p)):
+        raise NativeError(host().aby3h_sim_last_error().decode())
+    return X, Y, m
+
+
+def linear_dataset(n: int, dim: int = 128, D: int = 16):
+    """The linear-regression dataset (LinearModelGen, fixed point D):
+    (X [n][dim], Y [n] = X model + noise, model [dim])."""
+    import numpy as np
+
+    X = np.zeros((n, dim), np.int64)
+    Y = np.zeros(n, np.int64)
+    m = np.zeros(dim, np.float64)
+    if host().aby3h_linear_dataset(n, dim, D, X.ctypes.data_as(c_void_p), Y.ctypes.data_as(c_void_p),
+                                   m.ctypes.data_as(c_void_p)):
         raise NativeError(host().aby3h_sim_last_error().decode())
     return X, Y, m
 

@@ -206,6 +206,27 @@ int aby3h_sim_lr(int device, uint64_t n, uint64_t d, uint64_t B, uint64_t D, uin
 int aby3h_lr_dataset(uint64_t n, uint64_t dim, uint64_t D, int64_t* X, int64_t* Y, double* model);
 int aby3h_lr_batches(uint64_t n, uint64_t B, uint64_t iters, uint64_t* out);
 
+/* `iters` SGD_Linear iterations (aby3-ML/Regression.h:145-168), seeds, input
+ * order (party 0 shares X, Y, w = 0) and arguments as aby3h_sim_lr. */
+int aby3h_sim_linear(int device, uint64_t n, uint64_t d, uint64_t B, uint64_t D, uint64_t aB, uint64_t iters,
+                     const int64_t* X, const int64_t* Y, const uint64_t* batches, int64_t* out_w_shares,
+                     int64_t* out_w_plain);
+/* test_linearModel (kind 0) / test_logisticModel (kind 1) (Regression.h:
+ * 94-107, 188-214) of the model w [d] on (X [n][d], Y [n]), all fixed point D,
+ * by three parties seeded as aby3ML::init; party 0 shares X, Y, w in that
+ * order. out_pred_shares [party][share][n] and out_pred_plain [n]: the
+ * prediction mul(X, w) (kind 1: logisticFunc of it); out_l2_shares
+ * [party][share][1]: l2 = mul(err^T, err); out_score [2]: the function's
+ * return values {reveal(l2) / n, accuracy} (kind 0: out_score[1] = 0). NULL
+ * outputs are skipped. */
+int aby3h_sim_model_score(int device, int kind, uint64_t n, uint64_t d, uint64_t D, const int64_t* X,
+                          const int64_t* Y, const int64_t* w, int64_t* out_pred_shares, int64_t* out_pred_plain,
+                          int64_t* out_l2_shares, double* out_score);
+/* The LinearModelGen dataset of main-linear.cpp:37-51 in fixed point D (CPU
+ * only): X [n][dim], Y [n] = X model + noise, the model [dim]; NULL outputs
+ * skipped. The first k rows of an n-row draw are the k-row draw. */
+int aby3h_linear_dataset(uint64_t n, uint64_t dim, uint64_t D, int64_t* X, int64_t* Y, double* model);
+
 #ifdef __cplusplus
 }
 #endif

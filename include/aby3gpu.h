@@ -261,15 +261,34 @@ int aby3g_mfma_turn(int on);
  * device. Default 1. Plans (and aby3g_mul_workspace_bytes) depend on it. */
 int aby3g_set_gemm_sharing(int parties);
 
+/* The streaming skinny route of GEMM-mode products with N <= 8 columns (a
+ * tall share matrix times a few share columns, or a long dot product): one
+ * pass over A on the VALU instead of k_small_gemm's one wave per output or the
+ * MFMA path's digit image. Two forms: "long" when K >= 2^14 and M N <= 1024
+ * (K split over workgroups, the partial slabs summed by the epilogue pass),
+ * else "tall" (rows streamed, the product written in place).
+ *   mode 0 (default): automatic -- the long form wherever it applies, the
+ *           tall form beyond 2^23 product terms when K N <= 2048 (B fits
+ *           LDS); every other shape keeps the small / MFMA kernels;
+ *   mode 1: never (the small / MFMA kernels only);
+ *   mode 2: always, whenever N <= 8 (tests: tiny shapes reach the kernels).
+ * Process-wide (not per thread: co-located parties run on their own threads).
+ * Results are bit-identical under every mode; aby3g_mul_workspace_bytes and
+ * aby3g_mul_prefers_fused follow the mode in force when they are called. */
+int aby3g_skinny_route(int mode);
+
 /* 1 when the whole round-1 local part runs best as one fused launch
- * (aby3g_mul_trunc_local / aby3g_mul_local with zs): Hadamard, and GEMMs of
- * up to 2^23 product terms, which run on the VALU instead of the int8-MFMA
- * digit GEMM. 0 when the truncation pair should be overlapped on a second
- * stream (aby3g_trunc_tuple + aby3g_mul_sub_local). */
+ * (aby3g_mul_trunc_local / aby3g_mul_local with zs): Hadamard, GEMMs of
+ * up to 2^23 product terms, and GEMMs on the skinny route, which all run on
+ * the VALU instead of the int8-MFMA digit GEMM. 0 when the truncation pair
+ * should be overlapped on a second stream (aby3g_trunc_tuple +
+ * aby3g_mul_sub_local). */
 int aby3g_mul_prefers_fused(int mode, uint64_t M, uint64_t K, uint64_t N);
 
-/* Scratch needed by aby3g_mul_local / aby3g_mul_trunc_local (0 for Hadamard
- * and small GEMMs). */
+/* Scratch needed by aby3g_mul_local / aby3g_mul_trunc_local /
+ * aby3g_mul_sub_local: 0 for Hadamard, small GEMMs and the tall skinny form;
+ * the split-K slabs for the long skinny form; digit images and slabs for the
+ * MFMA path. */
 size_t aby3g_mul_workspace_bytes(int mode, uint64_t M, uint64_t K, uint64_t N);
 
 /* asyncMul without truncation, local part (Sh3Evaluator.cpp:92-116):
